@@ -496,8 +496,9 @@ def plain_loss_parity(tr, plans):
             "gates": {"loss_err<=1e-4*(CE+|Dice|)": err <= 1e-4 * terms, "loss_rel_err<=1e-3": rel <= 1e-3}}
 
 
-def build_trainer(workload, device, rank):
-    """Trainer of one BASELINE.json configuration in the state its timed iteration needs (second task for the CL methods)."""
+def build_trainer(workload, device, rank, deterministic_wgrad=False):
+    """Trainer of one BASELINE.json configuration in the state its timed iteration needs (second task for the CL methods).
+    ``deterministic_wgrad``: ordered weight-gradient reductions instead of the shipped fp32 atomics (--dump-outputs runs)."""
     import torch
     from lifelong_nnunet_amd import get_trainer_class
     plans, ext, wl_desc = WORKLOADS[workload]
@@ -511,7 +512,8 @@ def build_trainer(workload, device, rank):
         return ResidentBatches(make() if split == "train" else make, device, n=2)
 
     kw = {"cases_per_task": 8} if ext == "rehearsal_ewc" else {}
-    tr = Trainer("seg_outputs", "synthetic_task_A", plans=plans, data_provider=provider, device=device, fold=0, **kw)
+    tr = Trainer("seg_outputs", "synthetic_task_A", plans=plans, data_provider=provider, device=device, fold=0,
+                 deterministic_wgrad=deterministic_wgrad, **kw)
     tr.initialize(True, num_epochs=1000)
     tr.network.train()
     extra_cfg = {}
@@ -547,6 +549,47 @@ def build_trainer(workload, device, rank):
 def heaviest_block(eng):
     from lifelong_nnunet_amd.engine import ConvBlock
     return max((b for b in eng.order if isinstance(b, ConvBlock) and b.cin > 1), key=lambda b: b.z.V * b.cin * b.cout)
+
+
+DUMP_BYTES = 60_000_000       # --dump-outputs writes at most this much in all
+
+
+def capture_forward_outputs(tr, into):
+    """For the next iteration(s): the logits the trainer hands to its loss, kept in ``into["outputs"]``.  References only, no
+    device work in the timed step: every forward allocates its logits and backward only reads them (the loss writes its
+    gradients into buffers of its own).  Wraps ``on_forward_done`` on the instance; ``del tr.on_forward_done`` restores the
+    class's hook."""
+    orig = tr.on_forward_done
+
+    def hook(data, output, do_backprop):
+        into["outputs"] = [o.detach() for o in (output if isinstance(output, (tuple, list)) else (output,))]
+        return orig(data, output, do_backprop)
+    tr.on_forward_done = hook
+
+
+def write_dump(dirname, arrays, budget_bytes=DUMP_BYTES):
+    """``arrays``: name -> tensor / ndarray / number.  Writes ``dirname/<name>.npy`` (float64 for scalars, float32 otherwise).
+    An array above its share of ``budget_bytes`` is replaced by a fixed sample of its flattened elements (seeded, sorted
+    indices: the same positions for the same shape in every run).  Returns {name: (elements, sampled)}."""
+    import numpy as np
+    import torch
+    small = {k: np.asarray([float(v)], np.float64) for k, v in arrays.items() if np.ndim(v) == 0 and not torch.is_tensor(v)}
+    big = {k: v for k, v in arrays.items() if k not in small}
+    cap = max(1, (budget_bytes - 8 * len(small)) // 4 // max(1, len(big)))
+    out = dict(small)
+    info = {k: (1, False) for k in small}
+    for name, v in big.items():
+        t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+        n = t.numel()
+        if n > cap:
+            idx = np.sort(np.random.default_rng(0).choice(n, size=cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.float().cpu().numpy()
+        info[name] = (n, n > cap)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return info
 
 
 def other_workload(workload, args, device, rank):
@@ -619,6 +662,12 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="ranks beyond torch.cuda.device_count() reuse the visible GPUs round-robin (gloo only: a plumbing check "
                          "of the N-rank path on a 1-GPU box, never a measurement)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, gradient norm, the logits of every "
+                         "deep-supervision level, the updated parameters) as DIR/<name>.npy, rank 0, at most 60 MB: larger "
+                         "arrays as a fixed seeded sample.  The run uses the ordered weight-gradient reductions "
+                         "(deterministic_wgrad: bit-identical outputs run after run; its ms_per_step is that mode's, "
+                         "not the shipped path's)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -667,7 +716,9 @@ def main():
         dist.init_process_group(args.backend, rank=rank, world_size=world)
 
     from lifelong_nnunet_amd import native as nat
-    tr, plans, ext, wl_desc, extra_cfg = build_trainer(args.workload, device, rank)
+    # --dump-outputs: warm-up and timed steps run the ordered weight-gradient reductions (bit-identical run after run, so two
+    # builds can be compared output for output); without it the shipped path with its fp32 atomics is measured
+    tr, plans, ext, wl_desc, extra_cfg = build_trainer(args.workload, device, rank, deterministic_wgrad=bool(args.dump_outputs))
 
     # The iterations are enqueued the way the trainer's own epoch loop runs them (nnUNetTrainerMultiHead._run_epoch_loop): the
     # loss / gradient-norm / found-inf triple of an iteration travels to the host asynchronously and is consumed when the NEXT
@@ -708,9 +759,12 @@ def main():
             sampler = None
     if world > 1:
         dist.barrier()
+    captured = {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i_ in range(args.steps):
+        if args.dump_outputs and i_ == args.steps - 1:
+            capture_forward_outputs(tr, captured)
         loss = step()
     loss = float(loss)                  # the last iteration's loss has arrived (all earlier ones were consumed on the way)
     torch.cuda.synchronize()
@@ -721,6 +775,16 @@ def main():
     if sampler is not None:
         sampler.__exit__(None, None, None)
         power = sampler.summary()
+    dumped = None
+    if args.dump_outputs:
+        del tr.on_forward_done
+        if rank == 0:
+            arrays = {"loss": loss, "grad_norm": tr.last_grad_norm}
+            arrays.update({f"output_{k}": o for k, o in enumerate(captured["outputs"])})      # full resolution first
+            arrays["params"] = torch.cat([p.detach().reshape(-1).float() for _, p in tr.network.named_parameters()])
+            dumped = write_dump(args.dump_outputs, arrays)
+            del arrays
+        captured.clear()
     eng.probe = None
     probe_ser = None
     if probe is not None and world == 1:      # extra steps on ONE rank would issue gradient all-reduces nobody answers
@@ -781,14 +845,20 @@ def main():
                                f"base {plans['base_num_features']}, {plans['num_classes']} logits",
                    "global_batch": B * world, "parallelism": f"dp{world}", "loss": float(loss),
                    "distinct_resident_batches": len(tr.tr_gen.items) if isinstance(tr.tr_gen, ResidentBatches) else None,
+                   "deterministic_wgrad": bool(eng.deterministic_wgrad),
                    "conv_gflop_per_patch": flops_patch / 1e9,
                    "conv_stack_tflops": patches_per_s / world * flops_patch / 1e12,
                    "conv_stack_frac_of_mfma_peak": patches_per_s / world * flops_patch / 1e12 / PEAK_MFMA_F16_TFLOPS},
     }
     out["config"].update(extra_cfg)
-    # every measurement switch that is set: empty = the shipped path
+    # every measurement switch that is set: empty and deterministic_wgrad false = the shipped path
     out["config"]["lnn_env"] = {k: v for k, v in sorted(os.environ.items()) if k.startswith("LNN_")}
     out["ms_per_step_rank_min"], out["ms_per_step_rank_max"] = min(rank_ms), max(rank_ms)
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "step": args.steps,
+                               "timed_path": "ordered weight-gradient reductions (config.deterministic_wgrad), not the shipped "
+                                             "fp32 atomics: time it without --dump-outputs",
+                               "arrays": {k: {"elements": n, "sampled": s} for k, (n, s) in sorted(dumped.items())}}
     if dp_report is not None:
         out["data_parallel"] = dp_report
     out["config"]["loss_fetch"] = "asynchronous: consumed by the next iteration's loss-scale decision (the trainer's epoch loop)"

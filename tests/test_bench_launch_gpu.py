@@ -24,6 +24,7 @@ def test_bench_gpus_2_launches_two_ranks():
     assert d["config"]["global_batch"] == 4 and d["config"]["parallelism"] == "dp2"
     assert d["backend"] == "gloo" and d["distinct_devices"] == 1
     assert d["value"] > 0 and d["steps"] == 2
+    assert d["config"]["deterministic_wgrad"] is False and "dump_outputs" not in d        # a plain run measures the shipped path
     # VERDICT r5 task 7: the N > 1 line says what the gradient exchange did
     dp = d["data_parallel"]
     assert dp["stream"] == "wgrad" and dp["bucket_mb"] == 32 and dp["buckets"] >= 1
@@ -46,6 +47,37 @@ def test_bench_data_parallel_switches_select_the_alternatives():
     dp = d["data_parallel"]
     assert dp["stream"] == "own" and dp["bucket_mb"] == 4 and dp["buckets"] == 6          # 22.4 MB arena of the 40x56x40 plan
     assert dp["buckets_sent_in_backward"] == 6 and dp["buckets_sent_by_finish"] == 0 and d["ranks_seen"] == 2
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """``--dump-outputs DIR``: after exactly ``--steps`` timed steps the last one's loss, gradient norm, logits of every
+    deep-supervision level and updated parameters are written as float arrays; a second run with the same arguments starts
+    from the same inputs and arrives at bit-identical numbers (a dump run uses the ordered weight-gradient reductions)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--workload", "c1", "--no-cpu-baseline", "--no-roofline", "--no-extras", "--other-workloads", "none",
+                            "--dump-outputs", str(tmp_path / name)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dump_outputs"]["step"] == 3 and d["config"]["deterministic_wgrad"]
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["grad_norm.npy", "loss.npy", "output_0.npy", "output_1.npy", "output_2.npy", "params.npy"]
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64e6
+        arr = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arr.values())
+        assert arr["output_0"].shape == (2, 3, 40, 56, 40) and arr["output_2"].shape == (2, 3, 10, 14, 10)
+        assert abs(float(arr["loss"][0]) - d["config"]["loss"]) <= 1e-6 * abs(d["config"]["loss"])
+        runs.append(arr)
+    # ordered weight-gradient reductions (no fp32 atomics): two runs are bit-identical
+    a, b = runs
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 def test_bench_refuses_a_world_that_is_not_gpus():

@@ -726,6 +726,27 @@ def test_bench_workload_plans_build_their_networks():
             assert abs(full / 1e9 - 3385.56) < 1.0
 
 
+def test_bench_dump_writes_float_arrays_within_its_budget(tmp_path):
+    """``bench.py --dump-outputs``: scalars as float64, arrays as float32 (shape kept when whole), an array above its share of the
+    byte budget as a sample at the same seeded positions in every run, and never more than the budget on disk."""
+    import bench
+    big = torch.arange(100000, dtype=torch.float64)
+    arrays = {"loss": 0.25, "grad_norm": np.float32(3.5), "small": torch.ones(2, 3, 4, dtype=torch.float16), "big": big}
+    info = bench.write_dump(str(tmp_path / "a"), arrays, budget_bytes=40000)
+    assert info == {"loss": (1, False), "grad_norm": (1, False), "small": (24, False), "big": (100000, True)}
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == set(arrays)
+    assert got["loss"].dtype == np.float64 and got["loss"].tolist() == [0.25] and got["grad_norm"].tolist() == [3.5]
+    assert got["small"].dtype == np.float32 and got["small"].shape == (2, 3, 4)
+    b = got["big"]
+    assert b.dtype == np.float32 and 0 < b.size < big.numel() and np.all(np.diff(b) > 0)     # sorted distinct positions
+    idx = np.sort(np.random.default_rng(0).choice(big.numel(), size=b.size, replace=False))
+    assert np.array_equal(b, big.numpy()[idx].astype(np.float32))                          # the input's values at the seeded positions
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) - 128 for f in os.listdir(tmp_path / "a")) <= 40000
+    bench.write_dump(str(tmp_path / "b"), arrays, budget_bytes=40000)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "big.npy")), b)
+
+
 def test_committed_counter_passes_belong_to_the_library_the_tree_builds():
     """bench.py quotes HBM bytes per launch / shader clock / matrix-pipe occupancy from committed rocprofv3 counter passes and only for
     the binary they were collected with (``so_sha256``).  The build is reproducible, so the library built from this tree is normally that
