@@ -2,18 +2,23 @@
 """Benchmark of the hot path: 3-D U-Net training iterations (nnUNetTrainerSequential.run_iteration) on
 synthetic 160x192x160 patches -- BASELINE.json configs[1] -- one process per GPU.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --workload c3|c4|c5        (the continual-learning configurations of BASELINE.json, see WORKLOADS)
 
 A "step" is one complete optimisation step (H2D-free: the patches are resident in HBM): forward, deep-supervised
 Dice+CE (+ the trainer's regulariser), scaled backward, gradient all-reduce (N > 1), clip 12, SGD-Nesterov, head re-sync,
-loss fetch.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement"); `config.h2d_inclusive` is the same loop with the
-batches arriving from pinned host memory (copy of batch i+1 overlapped with step i), `regulariser_kernels` the HBM
-roofline of the flat-arena / logits kernels at the workload's sizes.
+loss fetch.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the steps,
+writes --dump-outputs and prints the line.  `--full` measures the rest as well (N = 1; --no-roofline, --no-cpu-baseline,
+--no-extras and --other-workloads leave parts out): `roofline` (the MFMA families probed inside the timed steps and
+isolated, board power, the vendor GEMM) and `regulariser_kernels` (the HBM roofline of the flat-arena / logits kernels
+at the workload's sizes), `config.eager_loss_fetch` and `config.h2d_inclusive` (the same loop with a synchronising loss
+fetch / with the batches arriving from pinned host memory), the CPU oracle's `cpu_baseline` and `parity`, and the
+`other_workloads` c3, c4, c5 and prostate after a c2 run.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -496,6 +501,47 @@ def plain_loss_parity(tr, plans):
             "gates": {"loss_err<=1e-4*(CE+|Dice|)": err <= 1e-4 * terms, "loss_rel_err<=1e-3": rel <= 1e-3}}
 
 
+def avg_pool3d_by_slabs(x, kernel_size, stride=None, *args, **kwargs):
+    """``F.avg_pool3d`` with PyTorch's CPU kernel run on depth slabs in a thread pool.  That kernel splits its work over the
+    N x C slices only, so the smoothing of a synthetic patch (``synthetic._smooth_field``: three box filters of up to 11^3 over
+    one 1 x 1 x 160x192x160 field) ran on one core: 15 s per C2 batch, most of a run's set-up.  Each slab carries its
+    ``kernel_size - 1`` halo planes, and every output element is the same kernel's sum over the same window: bit-identical.
+    Any other call (not 5-D on the CPU, several slices, a stride other than 1, further options) goes to ``F.avg_pool3d``."""
+    import torch
+    import torch.nn.functional as F
+    from concurrent.futures import ThreadPoolExecutor
+    if (args or kwargs or stride != 1 or not isinstance(kernel_size, int) or x.dim() != 5 or x.device.type != "cpu"
+            or x.shape[0] * x.shape[1] != 1):
+        return F.avg_pool3d(x, kernel_size, stride, *args, **kwargs)
+    n = min(torch.get_num_threads(), x.shape[2] - kernel_size + 1)
+    if n < 2:
+        return F.avg_pool3d(x, kernel_size, 1)
+    cut = [(x.shape[2] - kernel_size + 1) * j // n for j in range(n + 1)]       # output planes of slab j: cut[j] .. cut[j+1]-1
+    with ThreadPoolExecutor(n) as pool:
+        slabs = list(pool.map(lambda j: F.avg_pool3d(x[:, :, cut[j]:cut[j + 1] + kernel_size - 1], kernel_size, 1), range(n)))
+    return torch.cat(slabs, 2)
+
+
+class _FunctionalWithSlabPooling:
+    """``torch.nn.functional`` as seen by ``lifelong_nnunet_amd.synthetic`` inside ``synthetic_patches_on_all_cores``."""
+
+    def __getattr__(self, name):
+        import torch.nn.functional as F
+        return avg_pool3d_by_slabs if name == "avg_pool3d" else getattr(F, name)
+
+
+@contextlib.contextmanager
+def synthetic_patches_on_all_cores():
+    """Synthetic batches generated in this block pool through ``avg_pool3d_by_slabs``: the same numbers, on every core."""
+    from lifelong_nnunet_amd import synthetic
+    keep = synthetic.F
+    synthetic.F = _FunctionalWithSlabPooling()
+    try:
+        yield
+    finally:
+        synthetic.F = keep
+
+
 def build_trainer(workload, device, rank, deterministic_wgrad=False):
     """Trainer of one BASELINE.json configuration in the state its timed iteration needs (second task for the CL methods).
     ``deterministic_wgrad``: ordered weight-gradient reductions instead of the shipped fp32 atomics (--dump-outputs runs)."""
@@ -514,7 +560,8 @@ def build_trainer(workload, device, rank, deterministic_wgrad=False):
     kw = {"cases_per_task": 8} if ext == "rehearsal_ewc" else {}
     tr = Trainer("seg_outputs", "synthetic_task_A", plans=plans, data_provider=provider, device=device, fold=0,
                  deterministic_wgrad=deterministic_wgrad, **kw)
-    tr.initialize(True, num_epochs=1000)
+    with synthetic_patches_on_all_cores():
+        tr.initialize(True, num_epochs=1000)          # the training batches are generated here
     tr.network.train()
     extra_cfg = {}
     if ext in ("ewc", "rehearsal_ewc"):
@@ -527,8 +574,9 @@ def build_trainer(workload, device, rank, deterministic_wgrad=False):
         tr.network = tr.mh_network.assemble_model("synthetic_task_B")
         tr.task = "synthetic_task_B"
         if ext == "rehearsal_ewc":
-            gen, _ = tr.get_basic_generators()            # fused case list: task B + a seeded 25 % of task A
-            tr.tr_gen = ResidentBatches(gen, device, n=4)
+            with synthetic_patches_on_all_cores():
+                gen, _ = tr.get_basic_generators()            # fused case list: task B + a seeded 25 % of task A
+                tr.tr_gen = ResidentBatches(gen, device, n=4)
             extra_cfg["fused_train_cases"] = len(tr.dataset_tr)
             extra_cfg["batches_with_a_rehearsed_case"] = sum(any(str(k).startswith("synthetic_task_A") for k in it["keys"]) for it in tr.tr_gen.items)
         tr.loss.update_ewc_params(tr.fisher, tr.params)
@@ -648,14 +696,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures (roofline, regulariser kernels, loss-fetch "
+                         "and H2D-inclusive repeats, CPU baseline and parity, other workloads); the --no-* options below and "
+                         "--other-workloads leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline / parity blocks")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline / regulariser-kernel blocks")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the warm-up and the timed steps (no synchronising-fetch / H2D-inclusive repeats): counter passes")
+                    help="--full without the synchronising-fetch / H2D-inclusive repeats")
     ap.add_argument("--cpu-sample", default="full", choices=["full", "small"],
-                    help="CPU baseline / parity patch: one full-size patch (~15 s of CPU work) or a 128^3 sub-patch")
+                    help="--full's CPU baseline / parity patch: one full-size patch (~15 s of CPU work) or a 128^3 sub-patch")
     ap.add_argument("--other-workloads", default=None,
-                    help="comma list of further configurations reported as extra keys (default: c3,c4,c5,prostate with --workload c2 at N=1; 'none')")
+                    help="--full: comma list of further configurations reported as extra keys (default: c3,c4,c5,prostate with "
+                         "--workload c2 at N=1; 'none')")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the gradient exchange: nccl (= RCCL over xGMI, one GPU per rank) or gloo "
                          "(stages device tensors through host memory; what lets N ranks share one GPU in the tests)")
@@ -669,6 +722,12 @@ def main():
                          "(deterministic_wgrad: bit-identical outputs run after run; its ms_per_step is that mode's, "
                          "not the shipped path's)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the dump and the line -- every part of --full switched off
+        if args.other_workloads not in (None, "none"):
+            ap.error("--other-workloads measures further configurations: add --full")
+        args.no_cpu_baseline = args.no_roofline = args.no_extras = True
+        args.other_workloads = "none"
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: become the launcher -- one process per GPU under torch.distributed.run, same arguments
@@ -869,14 +928,15 @@ def main():
         tr.defer_loss_fetch = True
         out["config"]["eager_loss_fetch"] = {"ms_per_step": dt_e / args.steps * 1e3, "value": B * args.steps / dt_e,
                                              "how": "run_iteration's default: one synchronising device-to-host copy per iteration"}
-    if ext == "lwf":          # the fix behind a flag: every head evaluated on the training batch (one batch, one body pass)
+    if ext == "lwf":
+        out["config"]["note"] = ("value = reference semantics (T+2 batches per iteration, one extra eval forward per head); "
+                                 "conv_stack_* count the training pass only")
+    if ext == "lwf" and args.full:      # the fix behind a flag: every head evaluated on the training batch (one body pass)
         tr.same_batch_predictions = True
         timed(2)
         dt_sb, _ = timed(args.steps)
         tr.same_batch_predictions = False
         out["config"]["same_batch_predictions_patches_per_s"] = B * args.steps / dt_sb
-        out["config"]["note"] = ("value = reference semantics (T+2 batches per iteration, one extra eval forward per head); "
-                                 "conv_stack_* count the training pass only")
     if world == 1 and ext != "lwf" and not args.no_extras:
         # H2D-inclusive variant of the same loop (MH.py:606-617 includes to_cuda in the iteration)
         try:

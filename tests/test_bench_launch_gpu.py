@@ -80,6 +80,41 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
         assert np.array_equal(a[k], b[k]), k
 
 
+_FULL_ONLY = ("roofline", "regulariser_kernels", "cpu_baseline", "parity", "other_workloads", "value_h2d_inclusive")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_leaves_the_rest_to_full():
+    """A plain run is set-up, warm-up, the timed steps and the line; ``--full`` adds the roofline, the regulariser kernels, the
+    loss-fetch and H2D-inclusive repeats and the CPU baseline with its parity gates to the same line."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--cpu-sample", "small", "--other-workloads", "none"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--workload", "c1"] + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "patches/s"
+        assert d["higher_is_better"] is True and d["config"]["deterministic_wgrad"] is False
+    assert not [k for k in _FULL_ONLY if k in plain] and "eager_loss_fetch" not in plain["config"]
+    assert "h2d_inclusive" not in plain["config"]
+    assert all(k in full for k in _FULL_ONLY if k != "other_workloads") and "eager_loss_fetch" in full["config"]
+    assert full["roofline"]["slowest_family"] in full["roofline"]["families"]
+    assert full["parity"]["gates"]["loss_rel_err<=1e-4"], full["parity"]
+
+
+def test_bench_other_workloads_need_full():
+    """Further configurations are part of ``--full``: asking a plain run for them is an error, not a silent no-op (CPU test)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--other-workloads", "c3"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--full" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
 def test_bench_refuses_a_world_that_is_not_gpus():
     """A launcher that exports WORLD_SIZE=1 while asking for 8 GPUs must not record a 1-GPU number as n_gpus 8 (CPU test)."""
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

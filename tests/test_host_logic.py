@@ -747,6 +747,29 @@ def test_bench_dump_writes_float_arrays_within_its_budget(tmp_path):
     assert np.array_equal(np.load(str(tmp_path / "b" / "big.npy")), b)
 
 
+def test_bench_slab_pooling_generates_the_same_patches():
+    """bench.py builds its trainers' synthetic batches with the box filters split into depth slabs on a thread pool: every pooled
+    field and every generated batch (data and each deep-supervision target) is bit-identical to the single-threaded generation, and
+    ``lifelong_nnunet_amd.synthetic`` sees ``torch.nn.functional`` again after the block."""
+    import torch.nn.functional as F
+    import bench
+    from lifelong_nnunet_amd import synthetic
+    g = torch.Generator().manual_seed(5)
+    for shape, k in (((1, 1, 34, 50, 34), 11), ((1, 1, 28, 44, 36), 5), ((1, 1, 12, 70, 40), 7), ((1, 1, 4, 9, 9), 3)):
+        x = torch.randn(shape, generator=g)
+        assert torch.equal(bench.avg_pool3d_by_slabs(x, k, 1), F.avg_pool3d(x, k, 1)), (shape, k)
+    x = torch.randn((2, 3, 9, 9, 9), generator=g)
+    assert torch.equal(bench.avg_pool3d_by_slabs(x, 3, 1), F.avg_pool3d(x, 3, 1))          # several slices: F.avg_pool3d itself
+    assert torch.equal(bench.avg_pool3d_by_slabs(x, 3), F.avg_pool3d(x, 3))
+    for args in ((2, (24, 40, 24), 3, 1, 3, 7, 2.0, None), (2, (20, 64, 48), 3, 2, 3, 9, 1.5, [[1, 2, 2], [1, 2, 2], [2, 2, 2]])):
+        ref = synthetic.make_patch_batch(*args)
+        with bench.synthetic_patches_on_all_cores():
+            got = synthetic.make_patch_batch(*args)
+        assert synthetic.F is F
+        assert torch.equal(got[0], ref[0]) and len(got[1]) == len(ref[1])
+        assert all(torch.equal(a, b) for a, b in zip(got[1], ref[1]))
+
+
 def test_committed_counter_passes_belong_to_the_library_the_tree_builds():
     """bench.py quotes HBM bytes per launch / shader clock / matrix-pipe occupancy from committed rocprofv3 counter passes and only for
     the binary they were collected with (``so_sha256``).  The build is reproducible, so the library built from this tree is normally that

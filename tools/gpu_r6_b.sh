@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 ulimit -c 0
 sha256sum lifelong-nnunet_amd/csrc/liblnn_hip.so | tee $OUT/so_sha256.txt
 timeout 1500 python -m pytest tests -q -m gpu --timeout=600 -x > $OUT/pytest_gpu.log 2>&1; grep -E "^FAILED|^ERROR|passed|failed" $OUT/pytest_gpu.log | tail -8
-timeout 600 python bench.py --other-workloads none --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench.err; tail -2 $OUT/bench.err | cut -c1-300
+timeout 600 python bench.py --full --other-workloads none --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench.err; tail -2 $OUT/bench.err | cut -c1-300
 python - <<PY
 import json
 try:

@@ -8,7 +8,7 @@ ulimit -c 0
 sha256sum lifelong-nnunet_amd/csrc/liblnn_hip.so | tee $OUT/so_sha256.txt
 timeout 1500 python -m pytest tests -q -m gpu --timeout=600 > $OUT/pytest_gpu.log 2>&1; grep -E "^FAILED|^ERROR|passed|failed" $OUT/pytest_gpu.log | tail -8
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 900 python bench.py > $OUT/bench_c2.json 2> $OUT/bench.err; tail -2 $OUT/bench.err | cut -c1-300
+timeout 900 python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench.err; tail -2 $OUT/bench.err | cut -c1-300
 python - <<PY
 import json
 try:
@@ -24,7 +24,7 @@ try:
 except Exception as e: print("ERR", e)
 PY
 d=/tmp/prof_$TAG; rm -rf $d
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d $d -o r -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline --other-workloads none > $OUT/prof_bench.json 2> $OUT/prof.err)
+(cd "$TMPDIR" && timeout 400 rocprofv3 --kernel-trace --stats -d $d -o r -- python $OLDPWD/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --other-workloads none > $OUT/prof_bench.json 2> $OUT/prof.err)
 db=$(find $d -name "*.db" | head -1)
 python tools/rocpd_stats.py $db > $OUT/kernel_stats.txt 2>&1; head -8 $OUT/kernel_stats.txt | cut -c1-170
 python tools/step_timeline.py $db --step 8 > $OUT/timeline.txt 2>&1; tail -4 $OUT/timeline.txt
